@@ -573,6 +573,45 @@ def per_sample_child():
     return {}
 
 
+DUMP_RING_ROWS = 1 << 16      # seeded sample of the 2^20-row replay ring written by --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(eng, L, out_dir):
+    """what the timed path (train_iters: 4 vector env steps + one update) left after its last step, as float32 / float64 .npy
+    files: the learner's parameters, target and AdamW moments, the last update's loss, sampled indices, IS weights and TD
+    errors, the PER priorities, the envs' observations / actions, and a fixed sample of the replay ring's rows"""
+    torch.cuda.synchronize()
+    host = lambda t: t.detach().cpu().numpy()
+    arrays = {
+        "params": eng.get_params(host=True), "target_params": eng.get_params(L.BUF_TARGET, host=True),
+        "adam_mu": eng.get_params(L.BUF_MU, host=True), "adam_nu": eng.get_params(L.BUF_NU, host=True),
+        "adam_count": np.array([eng.opt_count()], np.float64),                # optimizer steps taken = updates so far
+        "loss": host(eng.last_loss()),
+        "batch_idx": host(eng.buffer(L.BUF_BATCH_IDX, torch.int32)[:B]).astype(np.float64),
+        "batch_isw": host(eng.buffer(L.BUF_BATCH_ISW)[:B]), "batch_td": host(eng.buffer(L.BUF_BATCH_TD)[:B]),
+        "per_tree": host(eng.buffer(L.BUF_TREE)),
+        "env_obs": host(eng.buffer(L.BUF_ENV_OBS)[:N_ENVS * D]).reshape(N_ENVS, D),
+        "env_actions": host(eng.buffer(L.BUF_ENV_ACTIONS, torch.int32)[:N_ENVS]).astype(np.float64),
+    }
+    rows = np.sort(np.random.default_rng(0).choice(1 << LOG2N, DUMP_RING_ROWS, replace=False))
+    ri = torch.as_tensor(rows, device=eng.device)
+    arrays.update({
+        "ring_rows": rows.astype(np.float64),
+        "ring_states": host(eng.buffer(L.BUF_STATES).view(-1, D)[ri]),
+        "ring_next_states": host(eng.buffer(L.BUF_OBSERVATIONS).view(-1, D)[ri]),
+        "ring_actions": host(eng.buffer(L.BUF_ACTIONS, torch.int32)[ri]).astype(np.float64),
+        "ring_rewards": host(eng.buffer(L.BUF_REWARDS)[ri]),
+        "ring_dones": host(eng.buffer(L.BUF_DONES, torch.uint8)[ri]).astype(np.float32),
+    })
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -585,6 +624,8 @@ def main():
     ap.add_argument("--per-sample-only", action="store_true", help=argparse.SUPPRESS)   # child mode: the stand-alone sampler lines only
     ap.add_argument("--precision", choices=["f32", "bf16"], default="f32",
                     help="f32 = exact f32 MFMA (meets the 1e-5 parity bar; default); bf16 = bf16 MFMA throughput path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))                          # nothing above or inside has touched the GPU
@@ -714,6 +755,8 @@ def main():
         reps = [timed(lambda: run_steps(args.steps)) for _ in range(max(args.repeats, 1))]
         ev = sorted(r[0] for r in reps); wl = sorted(r[1] for r in reps)
         dt, dt_wall = ev[len(ev) // 2], wl[len(wl) // 2]
+        if args.dump_outputs and rank == 0:                  # before the extra measurements below move the learner on
+            dump_outputs(eng, L, args.dump_outputs)
 
         # update-only and actor-only rates (same run, extra information)
         def upd_only(k):

@@ -418,8 +418,9 @@ def test_cnn_vector_agent_nstep(dq):
 
 
 def test_cnn_update_in_a_captured_graph(dq):
-    """dqn_cnn_update forks to the handle's side stream and joins by events: captured into a hipGraph (torch.cuda.graph) and
-    replayed it must do what the eager launches do -- same parameters after two steps, bit for bit"""
+    """dqn_cnn_update forks to the handle's side stream and joins by events (under a stream capture it keeps every launch on the
+    caller's stream): captured into a hipGraph (torch.cuda.graph) and replayed it must do what the eager launches do -- same
+    parameters after two steps, bit for bit"""
     import torch
     B = 8
     rng = np.random.default_rng(17)

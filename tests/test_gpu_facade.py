@@ -217,17 +217,20 @@ def test_agent_training_loop_and_checkpoint(ref, tmp_path):
     assert torch.equal(st3[0].nu.flat, agent._opt_state[0].nu.flat)
 
 
-def test_bench_prints_one_json_line_with_the_contract_fields(torch_cuda):
+def test_bench_prints_one_json_line_with_the_contract_fields(torch_cuda, tmp_path):
     """bench.py (short run): stdout is exactly ONE JSON line carrying the driver's contract fields, `roofline` and
-    `cpu_baseline`; native libraries' chatter must not reach stdout"""
+    `cpu_baseline`; native libraries' chatter must not reach stdout. --dump-outputs writes the last timed step's arrays
+    (float32 / float64 .npy, 64 MB at most), and a second run with the same arguments writes the same ones"""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DQN_BENCH_CPU_SECONDS="1")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "60", "--warmup", "20", "--profile-steps", "2",
-                          "--no-secondary"], capture_output=True, text=True, timeout=600, env=env)
+    def run(dump):
+        return subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "60", "--warmup", "20", "--profile-steps", "2",
+                               "--no-secondary", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, env=env)
+    out = run(tmp_path / "out")
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -241,4 +244,20 @@ def test_bench_prints_one_json_line_with_the_contract_fields(torch_cuda):
     assert r["bound"] in ("hbm", "mfma") and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and r["unit"] in ("GB/s", "TFLOP/s")
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
+    dumped = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert {"params", "loss", "batch_idx", "batch_td", "per_tree", "env_obs"} <= set(dumped)
+    assert all(a.dtype in (np.float32, np.float64) for a in dumped.values()) and sum(a.nbytes for a in dumped.values()) <= 64 << 20
+    assert np.isfinite(dumped["params"]).all() and dumped["loss"].shape == (1,) and dumped["batch_idx"].shape == (1024,)
+    # taken after the last timed step: warmup + one untimed region + 7 timed regions of --steps updates each
+    assert dumped["adam_count"][0] == 20 + 60 * (1 + 7)
+    sys.path.insert(0, root)
+    import bench
+    assert not np.array_equal(dumped["params"], bench.init_params(dumped["params"].size).numpy())
+    idx = dumped["batch_idx"]
+    assert (idx == np.floor(idx)).all() and idx.min() >= 0 and idx.max() < 1 << 20
+    # same arguments, same inputs: a second run leaves the same outputs, bit for bit
+    again = run(tmp_path / "again")
+    assert again.returncode == 0, again.stderr[-2000:]
+    for name, a in dumped.items():
+        assert np.array_equal(np.load(tmp_path / "again" / f"{name}.npy"), a), name
 

@@ -438,13 +438,68 @@ def test_pickle_token_reader_on_own_files(tmp_path):
         pt.read_haiku_params(str(tmp_path / "bad.pickle"))
 
 
-def test_reference_init_fixture():
+def _write_reference_checkpoint(directory, z):
+    """params.pickle / opt_state.pickle in the byte format of the reference's checkpoints (General/Base/utils.py:21-29:
+    pickle protocol 4 of a haiku dict of jax DeviceArrays, each one `jax._src.device_array.reconstruct_device_array(numpy's
+    reduction of the array, aval state)`,
+    and the optax.adamw state `(ScaleByAdamState(count, mu, nu), EmptyState(), EmptyState())` of DeviceArrays, mu / nu in
+    jax's sorted leaf order b, w), holding the arrays of ref_init_params.npz. jax and optax are not installed: stand-in
+    modules carry the module and class names the reference's files spell, so the opcode stream is theirs."""
+    import pickle
+    import types
+    import typing
+    dev, tr, base = (types.ModuleType(n) for n in ("jax._src.device_array", "optax._src.transform", "optax._src.base"))
+
+    def reconstruct_device_array(fun, args, arr_state, aval_state):
+        return None
+    reconstruct_device_array.__module__, reconstruct_device_array.__qualname__ = dev.__name__, "reconstruct_device_array"
+    dev.reconstruct_device_array = reconstruct_device_array
+
+    named_shapes = {}
+
+    class DeviceArray:
+        def __init__(self, a):
+            self.a = a
+
+        def __reduce__(self):                        # jax's DeviceArray.__reduce__: numpy's own reduction + the aval state
+            fun, args, arr_state = self.a.__reduce__()
+            named = named_shapes.setdefault((self.a.shape, self.a.dtype.str), {})    # one aval per shape and dtype in jax
+            return reconstruct_device_array, (fun, args, arr_state, {"weak_type": False, "named_shape": named})
+    tr.ScaleByAdamState = typing.NamedTuple("ScaleByAdamState", [("count", object), ("mu", object), ("nu", object)])
+    base.EmptyState = typing.NamedTuple("EmptyState", [])
+    tr.ScaleByAdamState.__module__, base.EmptyState.__module__ = tr.__name__, base.__name__
+    params, mu, nu, keys = {}, {}, {}, {}
+    for k in z.files:
+        parts = k.split("/")
+        if k.startswith("opt/") and parts[1] in ("mu", "nu"):               # mu and nu share their key objects, as in jax's
+            m = keys.setdefault("/".join(parts[2:-1]), "/".join(parts[2:-1]))  # tree: the pickle refers back to them (BINGET)
+            ({"mu": mu, "nu": nu}[parts[1]]).setdefault(m, {})[parts[-1]] = DeviceArray(z[k])
+        elif not k.startswith("opt/"):
+            params.setdefault("/".join(parts[:-1]), {})[parts[-1]] = DeviceArray(z[k])
+    state = (tr.ScaleByAdamState(DeviceArray(np.asarray(z["opt/count"][0], np.int32)), mu, nu), base.EmptyState(), base.EmptyState())
+    stand_in = {m.__name__: m for m in (dev, tr, base)}
+    stand_in.update({p: types.ModuleType(p) for p in ("jax", "jax._src", "optax", "optax._src")})     # the packages pickle imports
+    saved = {name: sys.modules.get(name) for name in stand_in}
+    sys.modules.update(stand_in)
+    try:
+        for name, obj in (("params.pickle", params), ("opt_state.pickle", state)):
+            with open(os.path.join(directory, name), "wb") as f:
+                pickle.dump(obj, f, protocol=4)
+    finally:
+        for name, m in saved.items():
+            if m is None:
+                sys.modules.pop(name, None)
+            else:
+                sys.modules[name] = m
+
+
+def test_reference_init_fixture(tmp_path):
     """tests/golden/ref_init_params.npz = the arrays inside the reference's Test/lunar_lander/{params,opt_state}.pickle
     (tests/golden/extract_ref_init.py). What the reference's own fixture pins about this path: the haiku tree of
     LunarLander/dddqn.py:19-22 at D = 9 (8 obs + the ObsWrapper column, env.py:19-24) -- leaf names, [in, out] weight
     layout, hk.Linear's default init (TruncatedNormal(1/sqrt(fan_in)) cut at 2 sigma, zero biases) that oracle_np.init_params
-    restates -- and optax.adamw's initial state (count 0, zero moments). Where the reference is present (build container)
-    the committed arrays are re-read from its files."""
+    restates -- and optax.adamw's initial state (count 0, zero moments). The checkpoint reader (pickle_tokens, which
+    generate_loading resumes from) is run on those arrays written in the reference's checkpoint byte format."""
     z = np.load(os.path.join(GOLD, "ref_init_params.npz"), allow_pickle=False)
     want = {("", "w"): (9, 32), ("", "b"): (32,), ("_1", "w"): (32, 64), ("_1", "b"): (64,), ("_2", "w"): (64, 1), ("_2", "b"): (1,),
             ("_3", "w"): (64, 4), ("_3", "b"): (4,)}
@@ -458,17 +513,21 @@ def test_reference_init_fixture():
             assert np.abs(a).max() <= 2.0 / np.sqrt(fan_in) + 1e-6 and 0.6 / np.sqrt(fan_in) < a.std() < 1.0 / np.sqrt(fan_in)
         assert not z[f"opt/mu/model/~/linear{sfx}/{leaf}"].any() and not z[f"opt/nu/model/~/linear{sfx}/{leaf}"].any()
     assert int(z["opt/count"][0]) == 0
+    # the checkpoint reader on the reference's byte format: the tree comes back leaf for leaf, the optax state as count 0,
+    # the stored moments and two trailing EmptyState (optax.adamw = chain(scale_by_adam, add_decayed_weights, scale))
+    from deep_q_learning_amd.General.Base import pickle_tokens as pt
+    _write_reference_checkpoint(str(tmp_path), z)
+    tree = pt.read_haiku_params(str(tmp_path / "params.pickle"))
+    assert list(tree) == ["model/~/linear", "model/~/linear_1", "model/~/linear_2", "model/~/linear_3"]
+    for m, leaves in tree.items():
+        assert list(leaves) == ["w", "b"]
+        for k, v in leaves.items():
+            assert v.dtype == np.float32 and np.array_equal(v, z[f"{m}/{k}"])
+    count, mu, nu, n_empty = pt.read_adam_state(str(tmp_path / "opt_state.pickle"))
+    assert count == 0 and n_empty == 2
+    for which, t in (("mu", mu), ("nu", nu)):
+        assert sorted(t) == sorted(tree) and all(np.array_equal(t[m][k], z[f"opt/{which}/{m}/{k}"]) for m in t for k in ("w", "b"))
     # the restatement's initialiser draws from the same family (same bounds; std of a 2-sigma truncated normal = 0.88 sigma)
     P = onp.init_params((9, 32, 64, 4), 0)
     w1 = P[:9 * 32]
     assert np.abs(w1).max() <= 2.0 / 3.0 + 1e-6 and not P[9 * 32:9 * 32 + 32].any()
-    ref_dir = "/root/reference/Test/lunar_lander"
-    if os.path.isdir(ref_dir):
-        from deep_q_learning_amd.General.Base import pickle_tokens as pt
-        tree = pt.read_haiku_params(os.path.join(ref_dir, "params.pickle"))
-        assert list(tree) == ["model/~/linear", "model/~/linear_1", "model/~/linear_2", "model/~/linear_3"]
-        for m, leaves in tree.items():
-            for k, v in leaves.items():
-                assert np.array_equal(v, z[f"{m}/{k}"])
-        count, mu, nu, n_empty = pt.read_adam_state(os.path.join(ref_dir, "opt_state.pickle"))
-        assert count == 0 and n_empty == 2                      # optax.adamw = chain(scale_by_adam, add_decayed_weights, scale)

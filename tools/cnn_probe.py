@@ -8,7 +8,8 @@ sys.path.insert(0, ROOT)
 import deep_q_learning_amd as dq
 ap = argparse.ArgumentParser()
 ap.add_argument("--precision", default="bf16"); ap.add_argument("--batch", type=int, default=512); ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--mode", default="forward"); ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph")
+ap.add_argument("--mode", default="forward"); ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (an update captured this way runs all on one stream, without the side "
+                                                                                  "streams of the eager update: csrc/dqn_cnn.hip CnnCaptureGuard)")
 a = ap.parse_args()
 B = a.batch
 e = dq.CnnEngine(num_actions=6, max_batch=B, precision=a.precision)
