@@ -13,21 +13,39 @@ numerical step is a C-ABI call:
   update           dqn_cnn_update_replay  (gather, three forwards, TD rule, backward, AdamW; q_agent.py:146-169)
   write-back       dqn_per_update_sorted  with |delta|
 
-The env is synthetic (there is no ALE here and no network): frames are uniform u8 (Philox, drawn by the step kernel), rewards
-Irwin-Hall normals, dones Bernoulli(p_done) -- the shape of PongNoFrameskip-v4 after the usual wrappers, not its dynamics.
+By default the env is synthetic (there is no ALE here and no network): frames are uniform u8 (Philox, drawn by the step kernel),
+rewards Irwin-Hall normals, dones Bernoulli(p_done) -- the shape of PongNoFrameskip-v4 after the usual wrappers, not its dynamics.
+
+With env= a pixel vector env (frame_envs.py: reset() / step() on raw u8 images, e.g. Catch), act + env + add is Agent._run_episode
+(q_agent.py:171-207) for pixel envs:
+  act              dqn_cnn_env_act        CNN forward on the envs' current stacks + epsilon-greedy (same Philox stream as above)
+  env              env.step               on the host: the actions come back first (a sync a host env needs)
+  add              dqn_cnn_env_observe    ONE launch: raw images -> luma, max over the frame-skip pair, area resize to 84 x 84, the
+                                          four-frame stacks (reset ones restart from the new episode's first image), the ring rows
+The index step after it is the same as for the synthetic env.
+
+td_rule: "reference" (default) is the reference's TD rule as written, whose terminal target is q[a] + r (quirk Q3): a Q value
+that a terminal reward feeds moves by r on every update and never settles, so an env that pays at its terminal steps (Catch,
+Pong's points) cannot be learned with it. td_rule="standard" takes r there (dqn_cnn_set_td_rule).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from ...cnn import CnnEngine
 from ...engine import Engine, EngineConfig
+from .frame_envs import reset_slots
 
 
 class CnnVectorAgent:
     def __init__(self, n_envs=512, num_actions=6, capacity=1 << 14, batch_size=512, precision="bf16", gamma=0.99, epsilon=1.0,
                  epsilon_decay_rate=0.999, min_epsilon=0.1, train_frequency=4, replace_frequency=250, per_beta=0.4, p_done=0.01,
-                 lr=1e-4, seed=0, n_step=1, device=None):
+                 lr=1e-4, seed=0, n_step=1, device=None, env=None, td_rule="reference"):
+        if env is not None:
+            n_envs = int(env.n_envs)                                        # (a pixel env brings its own count)
+            if int(getattr(env, "A", num_actions)) != num_actions:
+                raise ValueError(f"num_actions = {num_actions} but the env has {env.A} actions")
         if capacity % n_envs:
             raise ValueError("capacity must be a multiple of n_envs (whole vector steps per ring lap)")
         if not 1 <= n_step <= 8 or n_step * n_envs > capacity:
@@ -38,11 +56,17 @@ class CnnVectorAgent:
         self.cnn = CnnEngine(num_actions=num_actions, max_batch=max(n_envs, batch_size), precision=precision, device=device)
         self.cnn.replay_init(capacity)
         self.cnn.set_optimizer(lr=lr)
+        self.cnn.set_td_rule(td_rule)                                       # "standard" to learn from rewards paid at terminal steps
         # the PER tree: a dqn_handle used as a positions-only index (dqn_per_index_advance; its own ring is one float per position)
         self.index = Engine(EngineConfig(obs_dim=1, hidden1=16, hidden2=16, num_actions=2, capacity=capacity, use_per=True,
                                          max_batch=max(n_envs, batch_size), seed=seed), device=device)
         dev = self.cnn.device
-        self.cnn.env_reset_synth(n_envs, seed)
+        self.env = env
+        if env is None:
+            self.cnn.env_reset_synth(n_envs, seed)
+        else:
+            self.cnn.env_reset_frames(env.reset(), seed)
+            self._actions = torch.empty((n_envs,), dtype=torch.int32, device=dev)
         self.td_abs = torch.empty((self.B,), dtype=torch.float32, device=dev)
         # r03: the index works on a stream of its own. Its launches (one per vector step, the draw, the write-back) depend on the CNN
         # stream only through |delta| (write-back after the update) and feed it only idx / isw (update after the draw): they run
@@ -63,9 +87,20 @@ class CnnVectorAgent:
         self.cnn.set_params(flat); self.cnn.set_params(flat if target_flat is None else target_flat, target=True)
 
     def env_step(self):
-        """one vector env step: act + synthetic transition + frame ring (one C-ABI call), then the index"""
+        """one vector env step: act + synthetic transition + frame ring (one C-ABI call), or act, env.step and the frame ring for a
+        pixel env; then the index"""
         n = self.n_envs
-        first = self.cnn.env_step_synth(self.epsilon, self.p_done)
+        if self.env is None:
+            first = self.cnn.env_step_synth(self.epsilon, self.p_done)
+        else:
+            a = self.cnn.env_act(self.epsilon, out=self._actions)
+            a_host = a.cpu().numpy()                                        # (a host env needs the actions: one sync per step)
+            frames, rewards, dones, reset_frames = self.env.step(a_host)
+            slot = reset_slots(dones, reset_frames, n)
+            rewards = np.asarray(rewards, np.float32)
+            if rewards.shape != (n,):
+                raise ValueError(f"rewards must have shape ({n},), got {rewards.shape}")
+            first = self.cnn.env_observe(frames, a, rewards, np.asarray(dones, bool), slot, reset_frames)
         assert first == (self.env_steps * n) % self.cnn.capacity, (first, self.env_steps)      # the two rings move in lockstep
         if self.n_step == 1:
             with torch.cuda.stream(self.ist):

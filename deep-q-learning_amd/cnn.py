@@ -13,6 +13,24 @@ from . import _lib as L
 from .engine import _DevView, _ptr
 
 
+def image_geometry(shape):
+    """(n, F, H, W, C) of a batch of raw env images u8 [n, F, H, W, C]; the F axis may be left out when F = 1 and the C axis when
+    C = 1 (a 4-d batch is [n, F, H, W] when its second extent is 1 or 2, since H >= 84, and [n, H, W, C] otherwise). Raises
+    ValueError outside F in {1, 2}, C in {1, 3}, 84 <= H, W <= 512 (dqn_cnn_env_reset_frames' limits)."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 5:
+        n, F, H, W, Cc = shape
+    elif len(shape) == 4:
+        (n, F, H, W), Cc = (shape, 1) if shape[1] in (1, 2) else ((shape[0], 1) + shape[1:3], shape[3])
+    elif len(shape) == 3:
+        (n, H, W), F, Cc = shape, 1, 1
+    else:
+        raise ValueError(f"env images must be [n, F, H, W, C] (F / C axes optional when 1), got shape {shape}")
+    if F not in (1, 2) or Cc not in (1, 3) or not (84 <= H <= 512 and 84 <= W <= 512):
+        raise ValueError(f"env images {shape}: need F in (1, 2), C in (1, 3), 84 <= H, W <= 512")
+    return n, F, H, W, Cc
+
+
 class CnnEngine:
     def __init__(self, num_actions: int = 6, max_batch: int = 512, precision: str = "bf16", device=None):
         if not torch.cuda.is_available():
@@ -28,10 +46,16 @@ class CnnEngine:
         n = C.c_int64()
         L.check(self.lib.dqn_cnn_param_count(self.h, C.byref(n)))
         self.param_count = n.value
+        self.env_n, self.env_geometry = 0, None           # pixel envs (env_reset_frames)
 
     def set_flags(self, flags: int):
         """diagnostics (tests): _lib.CNN_FLAG_FC_WIDE_TILE | CNN_FLAG_NO_SIDE_STREAM | CNN_FLAG_LAYERWISE_CONV; results stay bit-identical"""
         L.check(self.lib.dqn_cnn_set_flags(self.h, int(flags)))
+
+    def set_td_rule(self, rule):
+        """"reference" (default: q_learning_functions.py:58-59 as written, terminal target q[a] + r) or "standard" (terminal target r)
+        for update() / update_from_replay(); q_targets() keeps the reference's rule"""
+        L.check(self.lib.dqn_cnn_set_td_rule(self.h, {"reference": L.TD_REFERENCE, "standard": L.TD_STANDARD}[rule]))
 
     def comm_init_native(self):
         """the handle's own RCCL communicator (dqn_cnn_comm_init), as Engine.comm_init_native: rank 0 makes the unique id,
@@ -210,3 +234,78 @@ class CnnEngine:
         L.check(self.lib.dqn_cnn_update_replay(self.h, _ptr(idx), _ptr(w) if w is not None else None, float(gamma), int(n_step), int(n_envs), idx.numel(),
                                                _ptr(td_abs_out) if td_abs_out is not None else None, C.byref(loss) if want_loss else None, self._s()))
         return loss.value if want_loss else None
+
+    # ---- pixel envs: raw env images in, the device does the rest (dqn_cnn_env_reset_frames / _act / _observe)
+    def _upload(self, parts):
+        """parts: [(array or tensor, torch dtype, shape)] -> device tensors. Tensors already on this device are used in place; host
+        arrays are packed into one pinned staging buffer and go to the device in ONE non_blocking copy on the current stream (the
+        staging buffers are reused: the pinned one once the previous copy has left it, the device one in stream order)."""
+        out, host, off = [None] * len(parts), [], 0
+        for k, (x, dt, shape) in enumerate(parts):
+            if isinstance(x, torch.Tensor) and x.device == self.device:
+                out[k] = x.to(dt).reshape(shape).contiguous()
+                continue
+            a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+            a = np.ascontiguousarray(a.reshape(shape), dtype=torch.empty((), dtype=dt).numpy().dtype)
+            host.append((k, a, off, shape)); off += (a.nbytes + 255) // 256 * 256
+        if host:
+            if getattr(self, "_pin", None) is None or self._pin.numel() < off:
+                self._pin = torch.empty(max(off, 1 << 20), dtype=torch.uint8, pin_memory=True)
+                self._dstage = torch.empty(self._pin.numel(), dtype=torch.uint8, device=self.device)
+                self._pin_ev = None
+            if self._pin_ev is not None:
+                self._pin_ev.synchronize()
+            pin = self._pin.numpy()
+            for k, a, o, shape in host:
+                pin[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+            self._dstage[:off].copy_(self._pin[:off], non_blocking=True)
+            self._pin_ev = torch.cuda.Event(); self._pin_ev.record(torch.cuda.current_stream(self.device))
+            for k, a, o, shape in host:
+                out[k] = self._dstage[o:o + a.nbytes].view(parts[k][1]).view(shape)
+        return out
+
+    def env_reset_frames(self, frames, seed=0):
+        """reset() of n pixel envs (gym FrameStack.reset): frames u8 [n, F, H, W, C] (torch or numpy; image_geometry) fix the
+        geometry; every env's stack = its preprocessed first image four times. Needs replay_init with capacity % n == 0; ends the
+        synthetic envs"""
+        x = frames if isinstance(frames, torch.Tensor) else np.asarray(frames)
+        n, F, H, W, Cc = image_geometry(x.shape)
+        (x,) = self._upload([(x, torch.uint8, (n, F, H, W, Cc))])
+        L.check(self.lib.dqn_cnn_env_reset_frames(self.h, n, _ptr(x), F, H, W, Cc, int(seed), self._s()))
+        self.env_n, self.env_geometry = n, (F, H, W, Cc)
+
+    def env_act(self, epsilon, out=None):
+        """Agent._policy (q_agent.py:137-141) on the pixel envs' current stacks: device int32 [n] (Philox (seed, env step, env))"""
+        a = out if out is not None else torch.empty((self.env_n,), dtype=torch.int32, device=self.device)
+        L.check(self.lib.dqn_cnn_env_act(self.h, float(epsilon), _ptr(a), self._s()))
+        return a
+
+    def env_observe(self, frames, actions, rewards, dones, reset_slot=None, reset_frames=None):
+        """env.step's result into the frame ring (ONE launch): frames u8 [n, F, H, W, C], actions int32 [n], rewards f32 [n], dones
+        [n] (stored as f32), reset_slot int32 [n] (row of reset_frames [m, F, H, W, C] that starts env e's next episode, -1 = none;
+        None = no resets). Returns the ring row of env 0."""
+        n, geo = self.env_n, self.env_geometry
+        if geo is None:
+            raise RuntimeError("no pixel envs: call env_reset_frames first")
+        x = frames if isinstance(frames, torch.Tensor) else np.asarray(frames)
+        if image_geometry(x.shape) != (n,) + geo:
+            raise ValueError(f"frames {tuple(x.shape)} do not match the {n} envs' geometry (F, H, W, C) = {geo}")
+        m = 0
+        if reset_frames is not None and reset_slot is None and np.shape(reset_frames)[0]:
+            raise ValueError("reset_frames without reset_slot: say which env each reset image starts")
+        if reset_frames is not None and reset_slot is not None:
+            rf = reset_frames if isinstance(reset_frames, torch.Tensor) else np.asarray(reset_frames)
+            m = int(rf.shape[0])
+            if m and image_geometry(rf.shape)[1:] != geo:
+                raise ValueError(f"reset frames {tuple(rf.shape)} do not match the envs' geometry (F, H, W, C) = {geo}")
+        parts = [(x, torch.uint8, (n,) + geo), (actions, torch.int32, (n,)), (rewards, torch.float32, (n,)), (dones, torch.float32, (n,))]
+        if reset_slot is not None:
+            parts.append((reset_slot, torch.int32, (n,)))
+        if m:
+            parts.append((rf, torch.uint8, (m,) + geo))
+        dev = self._upload(parts)
+        slot = _ptr(dev[4]) if reset_slot is not None else None
+        first = C.c_int64(0)
+        L.check(self.lib.dqn_cnn_env_observe(self.h, _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]), _ptr(dev[3]), slot,
+                                             _ptr(dev[5]) if m else None, m, C.byref(first), self._s()))
+        return first.value

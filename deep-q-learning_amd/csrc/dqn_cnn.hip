@@ -256,6 +256,7 @@ k_cnn_layer(int M, const TI *__restrict__ in, const TI *__restrict__ in2, int im
 
 #include "dqn_cnn_trunk.h"
 #include "dqn_cnn_btrunk.h"
+#include "dqn_cnn_frames.h"
 
 // dueling head (dddqn.py:29-31) on the fc features [B][512]: 16 rows per workgroup, thread (row, j) runs the k-ascending fmaf
 // chain of output j (0 = val, 1.. = adv) from LDS images of the rows and of the j-major head weights [16][512];
@@ -640,7 +641,17 @@ k_cnn_dw(int M, int rows_per_slice, const TI *__restrict__ in, const TC *__restr
 // workgroup's share of the head leaves: 16 rows per workgroup = one slice of the head slabs
 //   hslab[blk][j][k] = sum_{its rows} a3[i][k] gd[i][j]   (j = 0: val, 1..A: adv),   hbslab[blk][j] = sum gd[i][j]
 // (k_cnn_reduce adds the slices in order); one loss partial per workgroup.
-struct CnnTdArgs { const float *nq, *nt; const int32_t *a; const float *r, *d; float gamma; float *td_abs; };     // nq == nullptr: targets are given
+struct CnnTdArgs { const float *nq, *nt; const int32_t *a; const float *r, *d; float gamma; float *td_abs; int rule; };     // nq == nullptr: targets are given
+// DQN_TD_STANDARD (dqn_cnn_set_td_rule): the taken action's target is r + (1 - d) gamma nt[a*], i.e. r at a terminal row -- the
+// reference's rule (td_row, quirk Q3) keeps q[a] + r there, which walks a terminal Q value by r on every update.
+__device__ __forceinline__ float td_row_standard(const float *q, const float *nq, const float *nt, int a, float r, float d, float gamma, int A,
+                                                 float *target_row) {
+    int astar = 0;
+    for (int k = 1; k < A; ++k) if (nq[k] > nq[astar]) astar = k;
+    const float t = r + (1.0f - d) * (gamma * nt[astar]);
+    for (int k = 0; k < A; ++k) target_row[k] = k == a ? t : q[k];
+    return t - q[a];
+}
 template <typename TC>
 __global__ void __launch_bounds__(256)
 k_cnn_head_bwd(const float *__restrict__ q, const float *__restrict__ targets, const float *__restrict__ isw, const TC *__restrict__ feat,
@@ -653,7 +664,8 @@ k_cnn_head_bwd(const float *__restrict__ q, const float *__restrict__ targets, c
             const int i = r0 + tid;
             float qr[16], nqr[16], ntr[16], tr[16];
             for (int k = 0; k < A; ++k) { qr[k] = q[(long long)i * A + k]; nqr[k] = td.nq[(long long)i * A + k]; ntr[k] = td.nt[(long long)i * A + k]; }
-            const float delta = td_row(qr, nqr, ntr, td.a[i], td.r[i], td.d[i], td.gamma, A, tr);
+            const float delta = td.rule == DQN_TD_STANDARD ? td_row_standard(qr, nqr, ntr, td.a[i], td.r[i], td.d[i], td.gamma, A, tr)
+                                                           : td_row(qr, nqr, ntr, td.a[i], td.r[i], td.d[i], td.gamma, A, tr);
             for (int k = 0; k < A; ++k) ltg[16 * tid + k] = tr[k];
             if (td.td_abs) td.td_abs[i] = fabsf(delta);
         }
@@ -963,6 +975,10 @@ struct dqn_cnn_handle {
     int flags = 0; hipStream_t side_kept = nullptr;    // dqn_cnn_set_flags (diagnostics)
     hipStream_t side2 = nullptr; hipEvent_t ev_side2 = nullptr;        // r03: conv3's / conv2's dW on a second side stream (beside the fc leaf's step on the first)
     int env_n = 0; uint64_t env_seed = 0; long long env_steps = 0; const uint8_t *env_cur = nullptr;   // dqn_cnn_env_*_synth
+    // the vector env: env_mode 0 = none, 1 = synthetic (dqn_cnn_env_*_synth), 2 = pixel frames (dqn_cnn_env_reset_frames /
+    // _act / _observe: the envs' current stacks in frm_cur, max_batch of them, preprocessing geometry frm)
+    int env_mode = 0; uint32_t *frm_cur = nullptr; FrmGeo frm{};
+    int td_rule = DQN_TD_REFERENCE;                    // dqn_cnn_set_td_rule: the TD rule of dqn_cnn_update / _update_replay
     void *comm = nullptr; int rank = 0, world = 1;     // dqn_cnn_comm_init: per-GPU learners, one gradient all-reduce per update
     hipStream_t comm_st = nullptr; hipEvent_t ev_fc = nullptr, ev_fc_done = nullptr;   // the fc leaf's all-reduce on a stream of its own (data-parallel update)
 };
@@ -1083,6 +1099,7 @@ extern "C" int dqn_cnn_destroy(dqn_cnn_handle *h) {
     if (h->ev_tgt) (void)hipEventDestroy(h->ev_tgt);
     if (h->arena) (void)hipFree(h->arena);
     if (h->ring_arena) (void)hipFree(h->ring_arena);
+    if (h->frm_cur) (void)hipFree(h->frm_cur);
     delete h;
     return DQN_OK;
 }
@@ -1159,6 +1176,15 @@ extern "C" int dqn_cnn_set_flags(dqn_cnn_handle *h, int32_t flags) {
     if (h->side && !h->side_kept) h->side_kept = h->side;
     h->side = (flags & DQN_CNN_FLAG_NO_SIDE_STREAM) ? nullptr : h->side_kept;
     h->flags = flags;
+    return DQN_OK;
+}
+
+/* The TD rule of dqn_cnn_update / dqn_cnn_update_replay: DQN_TD_REFERENCE (default; q_learning_functions.py:58-59 as written,
+ * quirks Q3 / Q4) or DQN_TD_STANDARD (terminal rows bootstrap nothing: target r). dqn_cnn_q_targets keeps the reference's rule. */
+extern "C" int dqn_cnn_set_td_rule(dqn_cnn_handle *h, int32_t rule) {
+    CNN_REQ(h, "null handle");
+    CNN_REQ(rule == DQN_TD_REFERENCE || rule == DQN_TD_STANDARD, "unknown TD rule");
+    h->td_rule = rule;
     return DQN_OK;
 }
 
@@ -1487,7 +1513,7 @@ static int cnn_update_impl(dqn_cnn_handle *h, const uint8_t *s, const int32_t *a
     cnn_forward_pair(h, DQN_NET_ONLINE, s, B, s2, B, h->q[0], st, nullptr, true, both);              // one pass; s's activations are rows [0, B)
     if (h->side) (void)hipStreamWaitEvent(st, h->ev_tgt, 0);
     // the TD rule (:55-60) is the first thing the head-backward kernel does with the three Q tensors
-    const CnnTdArgs td{h->q[0] + (size_t)B * h->A, h->q[2], a, r, d, gamma, td_abs_out};
+    const CnnTdArgs td{h->q[0] + (size_t)B * h->A, h->q[2], a, r, d, gamma, td_abs_out, h->td_rule};
     if (h->comm) {
         // per-GPU learners: backward without the early fc-leaf step, the gradient summed over the ranks (fc leaf beside
         // the backward, the rest behind it), then the optimizer with grad_scale = 1 / world
@@ -1539,6 +1565,7 @@ extern "C" int dqn_cnn_replay_init(dqn_cnn_handle *h, int64_t capacity) {
     h->stage_a = (int32_t *)c; c += ssc; h->stage_r = (float *)c; c += ssc; h->stage_d = (float *)c; c += ssc;
     CNN_TRY(hipMemset(h->ring_arena, 0, total));
     h->ring_cap = capacity; h->ring_counter = 0;
+    h->env_mode = 0; h->env_n = 0; h->env_cur = nullptr;                // a new ring ends either env (no dangling env_cur)
     return DQN_OK;
 }
 
@@ -1604,7 +1631,7 @@ k_cnn_synth_frames(uint8_t *__restrict__ dst, int n, unsigned long long seed, un
 extern "C" int dqn_cnn_env_reset_synth(dqn_cnn_handle *h, int32_t n, uint64_t seed, void *stream) {
     CNN_REQ(h && h->ring_arena, "no ring: call dqn_cnn_replay_init");
     CNN_REQ(n >= 1 && n <= h->max_batch && h->ring_cap % n == 0, "dqn_cnn_env_reset_synth: n must divide the ring capacity and fit max_batch");
-    h->env_n = n; h->env_seed = seed; h->env_steps = 0;
+    h->env_mode = 1; h->env_n = n; h->env_seed = seed; h->env_steps = 0;  // (ends the pixel envs)
     h->env_cur = h->stage_s2;                                           // (free until the first update stages a batch: by then the envs live in the ring)
     hipLaunchKernelGGL(k_cnn_synth_frames, dim3(1024), dim3(256), 0, (hipStream_t)stream, h->stage_s2, n, seed, 0x8000000000000000ull);
     CNN_TRY(hipGetLastError());
@@ -1616,7 +1643,7 @@ extern "C" int dqn_cnn_env_reset_synth(dqn_cnn_handle *h, int32_t n, uint64_t se
  * frame stacks (Philox policy stream (seed, step, env), as dqn_cnn_act), the synthetic transition, ReplayBuffer.add of the n
  * transitions at ring rows [first, first + n). first_index (optional): the row of env 0. */
 extern "C" int dqn_cnn_env_step_synth(dqn_cnn_handle *h, float epsilon, float p_done, int64_t *first_index, void *stream) {
-    CNN_REQ(h && h->ring_arena && h->env_n > 0, "no envs: call dqn_cnn_env_reset_synth");
+    CNN_REQ(h && h->ring_arena && h->env_mode == 1 && h->env_n > 0, "no synthetic envs: call dqn_cnn_env_reset_synth");
     hipStream_t st = (hipStream_t)stream;
     const int n = h->env_n;
     const long long pos = h->ring_counter % h->ring_cap;
@@ -1625,6 +1652,65 @@ extern "C" int dqn_cnn_env_step_synth(dqn_cnn_handle *h, float epsilon, float p_
                        h->env_seed, (unsigned long long)h->env_steps, p_done, h->q[0], h->A, epsilon, h->ring_a);
     CNN_TRY(hipGetLastError());
     h->env_cur = h->ring_s2 + pos * CNN_FRAME_BYTES;
+    if (first_index) *first_index = pos;
+    h->ring_counter += n; h->env_steps += 1;
+    return DQN_OK;
+}
+
+// ---- pixel envs (the env runs on the host or anywhere else; dqn_cnn_frames.h): raw u8 images [n][F][H][W][C] in, everything from
+// there to the filed transition on the device. Exclusive with the synthetic env: the one reset last is the one that steps.
+static int frm_geometry(int32_t F, int32_t H, int32_t W, int32_t C, FrmGeo *g) {
+    CNN_REQ((F == 1 || F == 2) && (C == 1 || C == 3) && H >= 84 && H <= FRM_MAX_HW && W >= 84 && W <= FRM_MAX_HW,
+            "pixel env geometry: F must be 1 or 2, C 1 or 3, and 84 <= H, W <= 512");
+    *g = FrmGeo{F, H, W, C, (long long)F * H * W * C};
+    return DQN_OK;
+}
+
+/* reset() of n pixel envs (gym FrameStack.reset): the preprocessed raw[e] in all four channels of env e's current stack. Needs the
+ * ring with capacity % n == 0 (a vector step never wraps inside it), as dqn_cnn_env_reset_synth; fixes the geometry (F, H, W, C) */
+extern "C" int dqn_cnn_env_reset_frames(dqn_cnn_handle *h, int32_t n, const uint8_t *raw, int32_t F, int32_t H, int32_t W, int32_t C, uint64_t seed, void *stream) {
+    CNN_REQ(h && h->ring_arena, "no ring: call dqn_cnn_replay_init");
+    CNN_REQ(raw, "null argument");
+    CNN_REQ(n >= 1 && n <= h->max_batch && h->ring_cap % n == 0, "dqn_cnn_env_reset_frames: n must divide the ring capacity and fit max_batch");
+    FrmGeo g;
+    const int rc = frm_geometry(F, H, W, C, &g); if (rc) return rc;
+    if (!h->frm_cur) {
+        hipError_t e = hipMalloc(&h->frm_cur, (size_t)h->max_batch * CNN_FRAME_BYTES);
+        if (e != hipSuccess) { h->frm_cur = nullptr; return dqn_set_error(DQN_ERR_NOMEM, (std::string("hipMalloc (env frame stacks): ") + hipGetErrorString(e)).c_str()); }
+    }
+    hipLaunchKernelGGL(k_cnn_frames_init, dim3(FRM_BANDS, n), dim3(256), 0, (hipStream_t)stream, raw, g, h->frm_cur);
+    CNN_TRY(hipGetLastError());
+    h->env_mode = 2; h->env_n = n; h->env_seed = seed; h->env_steps = 0; h->frm = g;
+    h->env_cur = nullptr;                                               // (ends the synthetic envs)
+    return DQN_OK;
+}
+
+/* Agent._policy (q_agent.py:137-141) for the pixel envs: the CNN on their current stacks, epsilon-greedy with the Philox policy
+ * stream (seed, env step, env) of dqn_cnn_act / dqn_cnn_env_step_synth; actions_out: device int32 [n] */
+extern "C" int dqn_cnn_env_act(dqn_cnn_handle *h, float epsilon, int32_t *actions_out, void *stream) {
+    CNN_REQ(h && h->env_mode == 2, "no pixel envs: call dqn_cnn_env_reset_frames");
+    CNN_REQ(actions_out, "null argument");
+    cnn_forward_pair(h, DQN_NET_ONLINE, (const uint8_t *)h->frm_cur, h->env_n, nullptr, 0, h->q[0], (hipStream_t)stream, nullptr, false);
+    launch_policy((hipStream_t)stream, h->q[0], h->env_n, h->A, epsilon, h->env_seed, (unsigned long long)h->env_steps, actions_out, nullptr);
+    CNN_TRY(hipGetLastError());
+    return DQN_OK;
+}
+
+/* env.step's result into the ring (q_agent.py:176-183 for n envs), ONE launch: preprocessing of the n step images raw and of the
+ * reset images reset_raw [m] (the first frames of new episodes), ReplayBuffer.add of (s, a, r, s', d) at rows [first, first + n),
+ * the envs' next stacks (reset_slot[e] in [0, m): that reset image in all four channels; otherwise -- also for any slot outside
+ * [0, m) -- s'). dones are what the ring stores (truncation included); reset_slot null = no resets. */
+extern "C" int dqn_cnn_env_observe(dqn_cnn_handle *h, const uint8_t *raw, const int32_t *actions, const float *rewards, const float *dones,
+                                   const int32_t *reset_slot, const uint8_t *reset_raw, int32_t m, int64_t *first_index, void *stream) {
+    CNN_REQ(h && h->ring_arena && h->env_mode == 2, "no pixel envs: call dqn_cnn_env_reset_frames");
+    CNN_REQ(raw && actions && rewards && dones, "null argument");
+    CNN_REQ(m >= 0 && (m == 0 || (reset_raw && reset_slot)), "reset images need reset_raw and reset_slot");
+    const int n = h->env_n;
+    const long long pos = h->ring_counter % h->ring_cap;
+    CNN_REQ(pos + n <= h->ring_cap, "the ring head is not at a whole vector step (dqn_cnn_replay_add of other sizes in between)");
+    hipLaunchKernelGGL(k_cnn_frames_observe, dim3(FRM_BANDS, n), dim3(256), 0, (hipStream_t)stream, raw, m ? reset_raw : nullptr, reset_slot, m, h->frm,
+                       actions, rewards, dones, h->frm_cur, (uint32_t *)h->ring_s, (uint32_t *)h->ring_s2, h->ring_a, h->ring_r, h->ring_d, pos);
+    CNN_TRY(hipGetLastError());
     if (first_index) *first_index = pos;
     h->ring_counter += n; h->env_steps += 1;
     return DQN_OK;

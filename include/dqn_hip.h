@@ -267,6 +267,12 @@ int dqn_cnn_destroy(dqn_cnn_handle *h);
  * mode's three convolutions as one kernel per layer (r02's) instead of the fused trunk kernel (r03) */
 enum dqn_cnn_flags { DQN_CNN_FLAG_FC_WIDE_TILE = 1, DQN_CNN_FLAG_NO_SIDE_STREAM = 2, DQN_CNN_FLAG_LAYERWISE_CONV = 4 };
 int dqn_cnn_set_flags(dqn_cnn_handle *h, int32_t flags);
+/* The TD rule of dqn_cnn_update / dqn_cnn_update_replay. DQN_TD_REFERENCE (the default) is q_learning_functions.py:58-59 as
+ * written: at a terminal row the taken action's target is q[a] + r (quirk Q3), which moves that Q value by r on every update and
+ * does not converge when rewards arrive at terminal steps (Catch, Pong's points). DQN_TD_STANDARD: r + (1 - d) gamma Q'[a*], i.e.
+ * r at a terminal row. dqn_cnn_q_targets always follows the reference. */
+enum dqn_td_rule { DQN_TD_REFERENCE = 0, DQN_TD_STANDARD = 1 };
+int dqn_cnn_set_td_rule(dqn_cnn_handle *h, int32_t rule);
 int dqn_cnn_param_count(const dqn_cnn_handle *h, int64_t *n);
 int dqn_cnn_set_params(dqn_cnn_handle *h, int which_net, const float *src, int src_is_host, void *stream);
 int dqn_cnn_forward(dqn_cnn_handle *h, int which_net, const uint8_t *frames, int32_t B, float *q, void *stream);
@@ -316,6 +322,21 @@ int dqn_cnn_replay_add(dqn_cnn_handle *h, const uint8_t *s, const int32_t *a, co
 int dqn_cnn_env_reset_synth(dqn_cnn_handle *h, int32_t n, uint64_t seed, void *stream);
 int dqn_cnn_env_step_synth(dqn_cnn_handle *h, float epsilon, float p_done, int64_t *first_index, void *stream);
 int dqn_cnn_replay_size_host(const dqn_cnn_handle *h, int64_t *size, int64_t *counter);
+/* Pixel envs (the env runs wherever it runs; the device does everything from its raw u8 frames to the filed transition).
+ * Images are [F][H][W][C] u8, F in {1, 2} (the last raw frames of a frame-skip step), C in {3, 1} (RGB / gray), 84 <= H, W <= 512:
+ * luma Y = (4899 R + 9617 G + 1868 B + 8192) >> 14, the max over the F frames, an exact integer area resize to 84 x 84 (the mean
+ * rounded half up), frame stacks [84][84][4] with channel 3 the newest (gym FrameStack).
+ *   reset_frames: needs the ring, n <= max_batch, capacity % n == 0; fixes the geometry; every env's stack = raw[e] four times.
+ *   act: the CNN on the current stacks + epsilon-greedy, Philox policy stream (seed, env step, env) as dqn_cnn_act; int32 [n].
+ *   observe: ONE launch files ring rows [first, first + n): s = the stack, a / r / d as given (d includes truncation), s' = the
+ *     stack shifted by one frame with raw[e] appended; the next stack is s', or reset_raw[reset_slot[e]] four times when
+ *     reset_slot[e] is in [0, m) (any other slot counts as -1; reset_slot may be null when m = 0).
+ * The synthetic and the pixel env share the handle's env state: each reset ends the other, dqn_cnn_replay_init ends both. */
+int dqn_cnn_env_reset_frames(dqn_cnn_handle *h, int32_t n, const uint8_t *raw, int32_t F, int32_t H, int32_t W, int32_t C,
+                             uint64_t seed, void *stream);
+int dqn_cnn_env_act(dqn_cnn_handle *h, float epsilon, int32_t *actions_out, void *stream);
+int dqn_cnn_env_observe(dqn_cnn_handle *h, const uint8_t *raw, const int32_t *actions, const float *rewards, const float *dones,
+                        const int32_t *reset_slot, const uint8_t *reset_raw, int32_t m, int64_t *first_index, void *stream);
 /* n_step = 1: the stored rows. n_step 2..8 with the rows stored step-major (n_envs rows per env step, capacity a multiple of
  * n_envs): the n-step transition that STARTS at each row -- s and a of the row, R = r_0 + gamma (r_1 + ...) cut after the first done,
  * s' of the last step, that done flag; sample only rows whose n - 1 successors are already in the ring. */
