@@ -24,6 +24,9 @@ With env= a pixel vector env (frame_envs.py: reset() / step() on raw u8 images, 
                                           four-frame stacks (reset ones restart from the new episode's first image), the ring rows
 The index step after it is the same as for the synthetic env.
 
+compact_replay=True (pixel envs only) stores each preprocessed frame once instead of two whole stacks per row
+(dqn_cnn_replay_init_compact): about 7.1 KB per transition instead of 56 KB, the same rows, counters and updates.
+
 td_rule: "reference" (default) is the reference's TD rule as written, whose terminal target is q[a] + r (quirk Q3): a Q value
 that a terminal reward feeds moves by r on every update and never settles, so an env that pays at its terminal steps (Catch,
 Pong's points) cannot be learned with it. td_rule="standard" takes r there (dqn_cnn_set_td_rule).
@@ -41,7 +44,9 @@ from .frame_envs import reset_slots
 class CnnVectorAgent:
     def __init__(self, n_envs=512, num_actions=6, capacity=1 << 14, batch_size=512, precision="bf16", gamma=0.99, epsilon=1.0,
                  epsilon_decay_rate=0.999, min_epsilon=0.1, train_frequency=4, replace_frequency=250, per_beta=0.4, p_done=0.01,
-                 lr=1e-4, seed=0, n_step=1, device=None, env=None, td_rule="reference"):
+                 lr=1e-4, seed=0, n_step=1, device=None, env=None, td_rule="reference", compact_replay=False):
+        if compact_replay and env is None:
+            raise ValueError("compact_replay needs a pixel env: the synthetic env draws whole independent stacks")
         if env is not None:
             n_envs = int(env.n_envs)                                        # (a pixel env brings its own count)
             if int(getattr(env, "A", num_actions)) != num_actions:
@@ -54,7 +59,7 @@ class CnnVectorAgent:
         self.epsilon, self.decay, self.min_eps = float(epsilon), float(epsilon_decay_rate), float(min_epsilon)
         self.train_frequency, self.replace_frequency, self.per_beta, self.p_done = int(train_frequency), int(replace_frequency), float(per_beta), float(p_done)
         self.cnn = CnnEngine(num_actions=num_actions, max_batch=max(n_envs, batch_size), precision=precision, device=device)
-        self.cnn.replay_init(capacity)
+        self.cnn.replay_init(capacity, compact=compact_replay)
         self.cnn.set_optimizer(lr=lr)
         self.cnn.set_td_rule(td_rule)                                       # "standard" to learn from rewards paid at terminal steps
         # the PER tree: a dqn_handle used as a positions-only index (dqn_per_index_advance; its own ring is one float per position)

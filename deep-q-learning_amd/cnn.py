@@ -197,10 +197,19 @@ class CnnEngine:
         L.check(self.lib.dqn_cnn_env_step_synth(self.h, float(epsilon), float(p_done), C.byref(first), self._s()))
         return first.value
 
-    def replay_init(self, capacity):
-        """ReplayBuffer.__init__ (replay_buffer.py:20-34) for frame stacks"""
-        L.check(self.lib.dqn_cnn_replay_init(self.h, int(capacity)))
-        self.capacity = int(capacity)
+    def replay_init(self, capacity, compact=False):
+        """ReplayBuffer.__init__ (replay_buffer.py:20-34) for frame stacks. compact=True: each preprocessed frame stored once
+        (dqn_cnn_replay_init_compact, about 8x smaller); fed by the pixel envs only (env_reset_frames / env_observe), and a reset
+        env's terminal frame is not kept (its s' channel 3 is the next episode's first frame, under d = 1)"""
+        fn = self.lib.dqn_cnn_replay_init_compact if compact else self.lib.dqn_cnn_replay_init
+        L.check(fn(self.h, int(capacity)))
+        self.capacity, self.compact = int(capacity), bool(compact)
+
+    def replay_bytes(self):
+        """device bytes of the ring's arena (ring + the update's staging buffers)"""
+        b = C.c_int64(0)
+        L.check(self.lib.dqn_cnn_replay_bytes(self.h, C.byref(b)))
+        return b.value
 
     def replay_add(self, s, a, r, s2, d):
         """ReplayBuffer.add (replay_buffer.py:58-65) for n transitions; returns the ring position of the first"""

@@ -916,6 +916,19 @@ constexpr int CNN_FRAME_BYTES = 84 * 84 * 4;
 // and the n-step transition that STARTS at the sampled row is put together here from the n rows row + k n_envs: its action, R =
 // r_0 + gamma (r_1 + gamma (...)) cut after the first done (Horner form, the arithmetic of nstep_row in dqn_actor.hip), that done
 // flag, s of the first and s' of the last row. The caller samples only rows whose n - 1 successors are in the ring.
+// The scalars of sample i (shared with the compact ring's gather, dqn_cnn_compact.h).
+__device__ __forceinline__ void cnn_gather_scalars(const int32_t *__restrict__ ring_a, const float *__restrict__ ring_r, const float *__restrict__ ring_d,
+                                                   long long row, long long cap, int n_step, int n_envs, float gamma, int i,
+                                                   int32_t *__restrict__ a, float *__restrict__ r, float *__restrict__ d) {
+    a[i] = ring_a[row];
+    float rr[8], dd[8];
+    for (int k = 0; k < n_step; ++k) { const long long q = (row + (long long)k * n_envs) % cap; rr[k] = ring_r[q]; dd[k] = ring_d[q]; }
+    int last = n_step - 1;
+    for (int k = n_step - 2; k >= 0; --k) if (dd[k] != 0.0f) last = k;      // first done in the window
+    float acc = rr[last];
+    for (int k = last - 1; k >= 0; --k) acc = rr[k] + gamma * acc;
+    r[i] = acc; d[i] = last == n_step - 1 ? dd[n_step - 1] : 1.0f;
+}
 __global__ void __launch_bounds__(256)
 k_cnn_gather(const uint8_t *__restrict__ ring_s, const uint8_t *__restrict__ ring_s2, const int32_t *__restrict__ ring_a, const float *__restrict__ ring_r,
              const float *__restrict__ ring_d, const int32_t *__restrict__ idx, int B, long long cap, int n_step, int n_envs, float gamma,
@@ -931,17 +944,9 @@ k_cnn_gather(const uint8_t *__restrict__ ring_s, const uint8_t *__restrict__ rin
     for (int u = 0; u < 7; ++u) { const int p = threadIdx.x + 256 * u; if (p < CNN_FRAME_BYTES / 16) v[u] = src[p]; }
 #pragma unroll
     for (int u = 0; u < 7; ++u) { const int p = threadIdx.x + 256 * u; if (p < CNN_FRAME_BYTES / 16) dst[p] = v[u]; }
-    if (part == 0 && threadIdx.x == 0) {
-        a[i] = ring_a[row];
-        float rr[8], dd[8];
-        for (int k = 0; k < n_step; ++k) { const long long q = (row + (long long)k * n_envs) % cap; rr[k] = ring_r[q]; dd[k] = ring_d[q]; }
-        int last = n_step - 1;
-        for (int k = n_step - 2; k >= 0; --k) if (dd[k] != 0.0f) last = k;      // first done in the window
-        float acc = rr[last];
-        for (int k = last - 1; k >= 0; --k) acc = rr[k] + gamma * acc;
-        r[i] = acc; d[i] = last == n_step - 1 ? dd[n_step - 1] : 1.0f;
-    }
+    if (part == 0 && threadIdx.x == 0) cnn_gather_scalars(ring_a, ring_r, ring_d, row, cap, n_step, n_envs, gamma, i, a, r, d);
 }
+#include "dqn_cnn_compact.h"
 
 // ------------------------------------------------------------------------------------ C ABI
 #define CNN_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return dqn_set_error(DQN_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); } while (0)
@@ -970,6 +975,10 @@ struct dqn_cnn_handle {
     void *ring_arena = nullptr; long long ring_cap = 0, ring_counter = 0;
     uint8_t *ring_s = nullptr, *ring_s2 = nullptr, *stage_s = nullptr, *stage_s2 = nullptr; int32_t *ring_a = nullptr, *stage_a = nullptr;
     float *ring_r = nullptr, *ring_d = nullptr, *stage_r = nullptr, *stage_d = nullptr;
+    long long ring_bytes = 0;                          // the arena's size (dqn_cnn_replay_bytes)
+    // compact ring (dqn_cnn_replay_init_compact, dqn_cnn_compact.h): no ring_s / ring_s2; frames once each in plane (plane_slots
+    // of 7056 bytes), per row the meta word slot | k << 30, per env k_env (its step within the episode, clamped to 3)
+    bool compact = false; uint8_t *plane = nullptr; long long plane_slots = 0; uint32_t *ring_meta = nullptr; int32_t *k_env = nullptr;
     hipStream_t side = nullptr; hipEvent_t ev_dz[4] = {nullptr}, ev_side = nullptr, ev_fork = nullptr, ev_tgt = nullptr;    // the dW kernels of layers 1..3 run beside the backward-data chain
     int adamw = 1; float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f, wd = 1e-4f;
     int flags = 0; hipStream_t side_kept = nullptr;    // dqn_cnn_set_flags (diagnostics)
@@ -1549,23 +1558,40 @@ extern "C" int dqn_cnn_act(dqn_cnn_handle *h, const uint8_t *frames, int32_t n, 
     return DQN_OK;
 }
 
-/* ReplayBuffer.__init__ (replay_buffer.py:20-34) for frame stacks: capacity rows of s, s' (u8), a, r, d; zeroed */
-extern "C" int dqn_cnn_replay_init(dqn_cnn_handle *h, int64_t capacity) {
+/* ReplayBuffer.__init__ (replay_buffer.py:20-34) for frame stacks: capacity rows of s, s' (u8), a, r, d; zeroed.
+ * compact (dqn_cnn_replay_init_compact): a frame plane of capacity + 4 max_batch slots and per row a, r, d, meta instead of s, s'.
+ * Either way the staging buffers of dqn_cnn_update_replay follow in the same arena. */
+static int cnn_ring_alloc(dqn_cnn_handle *h, int64_t capacity, bool compact) {
     CNN_REQ(h && capacity >= 1 && capacity <= ((int64_t)1 << 24), "dqn_cnn_replay_init: bad capacity");
     CNN_REQ(!h->ring_arena, "the ring exists already");
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const long long slots = capacity + 4LL * h->max_batch;
     const size_t fr = al((size_t)capacity * CNN_FRAME_BYTES), sc = al((size_t)capacity * 4), sfr = al((size_t)h->max_batch * CNN_FRAME_BYTES), ssc = al((size_t)h->max_batch * 4);
-    const size_t total = 2 * fr + 3 * sc + 2 * sfr + 3 * ssc;
+    const size_t pl = al((size_t)slots * STACK_PX);
+    const size_t total = compact ? pl + 4 * sc + 2 * sfr + 4 * ssc : 2 * fr + 3 * sc + 2 * sfr + 3 * ssc;
     hipError_t e = hipMalloc(&h->ring_arena, total);
     if (e != hipSuccess) { h->ring_arena = nullptr; return dqn_set_error(DQN_ERR_NOMEM, (std::string("hipMalloc (frame ring): ") + hipGetErrorString(e)).c_str()); }
     char *c = (char *)h->ring_arena;
-    h->ring_s = (uint8_t *)c; c += fr; h->ring_s2 = (uint8_t *)c; c += fr;
+    if (compact) { h->plane = (uint8_t *)c; c += pl; }
+    else { h->ring_s = (uint8_t *)c; c += fr; h->ring_s2 = (uint8_t *)c; c += fr; }
     h->ring_a = (int32_t *)c; c += sc; h->ring_r = (float *)c; c += sc; h->ring_d = (float *)c; c += sc;
+    if (compact) { h->ring_meta = (uint32_t *)c; c += sc; }
     h->stage_s = (uint8_t *)c; c += sfr; h->stage_s2 = (uint8_t *)c; c += sfr;
     h->stage_a = (int32_t *)c; c += ssc; h->stage_r = (float *)c; c += ssc; h->stage_d = (float *)c; c += ssc;
-    CNN_TRY(hipMemset(h->ring_arena, 0, total));
-    h->ring_cap = capacity; h->ring_counter = 0;
+    if (compact) { h->k_env = (int32_t *)c; c += ssc; }
+    CNN_TRY(hipMemset(h->ring_arena, 0, total));                       // (compact: meta 0 = slot 0, k 0 -- a never-written row gathers in bounds)
+    h->ring_cap = capacity; h->ring_counter = 0; h->ring_bytes = (long long)total;
+    h->compact = compact; h->plane_slots = compact ? slots : 0;
     h->env_mode = 0; h->env_n = 0; h->env_cur = nullptr;                // a new ring ends either env (no dangling env_cur)
+    return DQN_OK;
+}
+extern "C" int dqn_cnn_replay_init(dqn_cnn_handle *h, int64_t capacity) { return cnn_ring_alloc(h, capacity, false); }
+/* the compact frame ring (dqn_cnn_compact.h): each preprocessed frame stored once, about 7 072 bytes per row
+ * instead of 56 460; fed only by the pixel envs (dqn_cnn_env_reset_frames / _observe) */
+extern "C" int dqn_cnn_replay_init_compact(dqn_cnn_handle *h, int64_t capacity) { return cnn_ring_alloc(h, capacity, true); }
+extern "C" int dqn_cnn_replay_bytes(const dqn_cnn_handle *h, int64_t *bytes) {
+    CNN_REQ(h && bytes, "null argument");
+    *bytes = h->ring_bytes;
     return DQN_OK;
 }
 
@@ -1574,6 +1600,7 @@ extern "C" int dqn_cnn_replay_init(dqn_cnn_handle *h, int64_t capacity) {
 extern "C" int dqn_cnn_replay_add(dqn_cnn_handle *h, const uint8_t *s, const int32_t *a, const float *r, const uint8_t *s2, const float *d,
                                   int32_t n, int64_t *first_index, void *stream) {
     CNN_REQ(h && h->ring_arena, "no ring: call dqn_cnn_replay_init");
+    CNN_REQ(!h->compact, "dqn_cnn_replay_add on a compact ring: it stores frames, not stacks; feed it with dqn_cnn_env_observe");
     CNN_REQ(s && a && r && s2 && d && n >= 1 && n <= h->ring_cap, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     const long long pos = h->ring_counter % h->ring_cap, n1 = (pos + n <= h->ring_cap) ? n : h->ring_cap - pos, n2 = n - n1;
@@ -1630,6 +1657,7 @@ k_cnn_synth_frames(uint8_t *__restrict__ dst, int n, unsigned long long seed, un
  * needs the ring (dqn_cnn_replay_init) with capacity % n == 0 so that a vector step never wraps inside the ring */
 extern "C" int dqn_cnn_env_reset_synth(dqn_cnn_handle *h, int32_t n, uint64_t seed, void *stream) {
     CNN_REQ(h && h->ring_arena, "no ring: call dqn_cnn_replay_init");
+    CNN_REQ(!h->compact, "the synthetic envs draw whole stacks, which a compact ring cannot store: use dqn_cnn_replay_init");
     CNN_REQ(n >= 1 && n <= h->max_batch && h->ring_cap % n == 0, "dqn_cnn_env_reset_synth: n must divide the ring capacity and fit max_batch");
     h->env_mode = 1; h->env_n = n; h->env_seed = seed; h->env_steps = 0;  // (ends the pixel envs)
     h->env_cur = h->stage_s2;                                           // (free until the first update stages a batch: by then the envs live in the ring)
@@ -1643,7 +1671,8 @@ extern "C" int dqn_cnn_env_reset_synth(dqn_cnn_handle *h, int32_t n, uint64_t se
  * frame stacks (Philox policy stream (seed, step, env), as dqn_cnn_act), the synthetic transition, ReplayBuffer.add of the n
  * transitions at ring rows [first, first + n). first_index (optional): the row of env 0. */
 extern "C" int dqn_cnn_env_step_synth(dqn_cnn_handle *h, float epsilon, float p_done, int64_t *first_index, void *stream) {
-    CNN_REQ(h && h->ring_arena && h->env_mode == 1 && h->env_n > 0, "no synthetic envs: call dqn_cnn_env_reset_synth");
+    CNN_REQ(h && h->ring_arena && !h->compact, "the synthetic envs draw whole stacks, which a compact ring cannot store: use dqn_cnn_replay_init");
+    CNN_REQ(h->env_mode == 1 && h->env_n > 0, "no synthetic envs: call dqn_cnn_env_reset_synth");
     hipStream_t st = (hipStream_t)stream;
     const int n = h->env_n;
     const long long pos = h->ring_counter % h->ring_cap;
@@ -1672,6 +1701,7 @@ extern "C" int dqn_cnn_env_reset_frames(dqn_cnn_handle *h, int32_t n, const uint
     CNN_REQ(h && h->ring_arena, "no ring: call dqn_cnn_replay_init");
     CNN_REQ(raw, "null argument");
     CNN_REQ(n >= 1 && n <= h->max_batch && h->ring_cap % n == 0, "dqn_cnn_env_reset_frames: n must divide the ring capacity and fit max_batch");
+    CNN_REQ(!h->compact || h->ring_counter == 0, "a compact ring takes one dqn_cnn_env_reset_frames before its first row: a reset later would overwrite frames the rows still use");
     FrmGeo g;
     const int rc = frm_geometry(F, H, W, C, &g); if (rc) return rc;
     if (!h->frm_cur) {
@@ -1679,6 +1709,8 @@ extern "C" int dqn_cnn_env_reset_frames(dqn_cnn_handle *h, int32_t n, const uint
         if (e != hipSuccess) { h->frm_cur = nullptr; return dqn_set_error(DQN_ERR_NOMEM, (std::string("hipMalloc (env frame stacks): ") + hipGetErrorString(e)).c_str()); }
     }
     hipLaunchKernelGGL(k_cnn_frames_init, dim3(FRM_BANDS, n), dim3(256), 0, (hipStream_t)stream, raw, g, h->frm_cur);
+    if (h->compact)                                                     // x_0 into the slots of the first rows, k_env = 0
+        hipLaunchKernelGGL(k_cnn_compact_seed, dim3(n), dim3(256), 0, (hipStream_t)stream, h->frm_cur, h->plane, h->plane_slots, h->ring_counter, h->k_env);
     CNN_TRY(hipGetLastError());
     h->env_mode = 2; h->env_n = n; h->env_seed = seed; h->env_steps = 0; h->frm = g;
     h->env_cur = nullptr;                                               // (ends the synthetic envs)
@@ -1708,8 +1740,13 @@ extern "C" int dqn_cnn_env_observe(dqn_cnn_handle *h, const uint8_t *raw, const 
     const int n = h->env_n;
     const long long pos = h->ring_counter % h->ring_cap;
     CNN_REQ(pos + n <= h->ring_cap, "the ring head is not at a whole vector step (dqn_cnn_replay_add of other sizes in between)");
-    hipLaunchKernelGGL(k_cnn_frames_observe, dim3(FRM_BANDS, n), dim3(256), 0, (hipStream_t)stream, raw, m ? reset_raw : nullptr, reset_slot, m, h->frm,
-                       actions, rewards, dones, h->frm_cur, (uint32_t *)h->ring_s, (uint32_t *)h->ring_s2, h->ring_a, h->ring_r, h->ring_d, pos);
+    if (h->compact)
+        hipLaunchKernelGGL(k_cnn_compact_observe, dim3(FRM_BANDS, n), dim3(256), 0, (hipStream_t)stream, raw, m ? reset_raw : nullptr, reset_slot, m, h->frm,
+                           actions, rewards, dones, h->frm_cur, h->k_env, h->plane, h->plane_slots, h->ring_a, h->ring_r, h->ring_d, h->ring_meta,
+                           pos, h->ring_counter, n);
+    else
+        hipLaunchKernelGGL(k_cnn_frames_observe, dim3(FRM_BANDS, n), dim3(256), 0, (hipStream_t)stream, raw, m ? reset_raw : nullptr, reset_slot, m, h->frm,
+                           actions, rewards, dones, h->frm_cur, (uint32_t *)h->ring_s, (uint32_t *)h->ring_s2, h->ring_a, h->ring_r, h->ring_d, pos);
     CNN_TRY(hipGetLastError());
     if (first_index) *first_index = pos;
     h->ring_counter += n; h->env_steps += 1;
@@ -1729,6 +1766,12 @@ extern "C" int dqn_cnn_replay_gather(dqn_cnn_handle *h, const int32_t *idx, int3
     CNN_REQ(h && h->ring_arena, "no ring: call dqn_cnn_replay_init");
     CNN_REQ(idx && s && a && r && s2 && d && B >= 1, "bad argument");
     CNN_REQ(n_step >= 1 && n_step <= 8 && (n_step == 1 || (n_envs >= 1 && h->ring_cap % n_envs == 0 && (long long)n_step * n_envs <= h->ring_cap)), "bad n_step / n_envs");
+    if (h->compact) {
+        hipLaunchKernelGGL(k_cnn_compact_gather, dim3(B, 2), dim3(256), 0, (hipStream_t)stream, h->plane, (int)h->plane_slots, h->ring_meta, h->ring_a, h->ring_r,
+                           h->ring_d, idx, B, h->ring_cap, n_step, n_step == 1 ? 0 : n_envs, h->env_n, gamma, s, s2, a, r, d);
+        CNN_TRY(hipGetLastError());
+        return DQN_OK;
+    }
     hipLaunchKernelGGL(k_cnn_gather, dim3(B, 2), dim3(256), 0, (hipStream_t)stream, h->ring_s, h->ring_s2, h->ring_a, h->ring_r, h->ring_d, idx, B, h->ring_cap,
                        n_step, n_step == 1 ? 0 : n_envs, gamma, s, s2, a, r, d);
     CNN_TRY(hipGetLastError());
@@ -1746,6 +1789,12 @@ extern "C" int dqn_cnn_update_replay(dqn_cnn_handle *h, const int32_t *idx, cons
     const CnnCaptureGuard cg(h, (hipStream_t)stream);
     float gn = gamma;
     for (int k = 1; k < n_step; ++k) gn = gn * gamma;                  // gamma^n as n - 1 f32 products
+    if (h->compact) {
+        // compact ring: the stacks exist only once assembled, so the gather runs first, on the caller's stream, into the staging
+        // buffers, which the update then reads as dqn_cnn_update's arguments (in bf16 mode: k_cnn_trunk16's DMA source)
+        int rc = dqn_cnn_replay_gather(h, idx, B, n_step, n_envs, gamma, h->stage_s, h->stage_a, h->stage_r, h->stage_s2, h->stage_d, stream); if (rc) return rc;
+        return cnn_update_impl(h, h->stage_s, h->stage_a, h->stage_r, h->stage_s2, h->stage_d, isw, gn, B, td_abs_out, loss_host, stream);
+    }
     if (cnn_trunk_fused(h)) {
         // r03 (bf16 mode): the trunk kernel reads the sampled rows where they lie in the ring (its DMA source address). What is left
         // of the gather -- action / n-step return / done, and the copy of s that conv1's weight gradient reads much later -- goes to

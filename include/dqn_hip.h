@@ -346,6 +346,18 @@ int dqn_cnn_replay_gather(dqn_cnn_handle *h, const int32_t *idx, int32_t B, int3
  * td_abs_out (device, optional) = |delta| per sample */
 int dqn_cnn_update_replay(dqn_cnn_handle *h, const int32_t *idx, const float *isw, float gamma, int32_t n_step, int32_t n_envs,
                           int32_t B, float *td_abs_out, float *loss_host, void *stream);
+/* The compact frame ring: the same rows, counters and valid rows as dqn_cnn_replay_init's ring fed the same
+ * dqn_cnn_env_observe calls, but each preprocessed 84x84 frame is stored once (about 7 072 bytes per row instead of 56 460; the
+ * stacks are put together by dqn_cnn_replay_gather / dqn_cnn_update_replay). Same capacity limits; the ring exists only once.
+ * It works with dqn_cnn_env_reset_frames (once, before the first row), _env_act, _env_observe, dqn_cnn_replay_gather,
+ * _update_replay and _replay_size_host; dqn_cnn_replay_add, the synthetic env and a later env reset are refused (DQN_ERR_INVALID).
+ * Gathers are bit-identical to the full ring's with one exception: a row whose env was reset (reset_slot[e] in [0, m)) keeps no
+ * terminal frame, so channel 3 of its s' is the next episode's first frame. Such rows must carry d = 1 (truncation included), and
+ * both TD rules multiply that term by (1 - d) = 0, so the update is bit-identical for finite Q -- except that a reward of exactly
+ * -0.0 on such a row may come out as +0.0 in delta. */
+int dqn_cnn_replay_init_compact(dqn_cnn_handle *h, int64_t capacity);
+/* device bytes of the ring's arena (the ring, its update's staging buffers; either mode; 0 before replay_init) */
+int dqn_cnn_replay_bytes(const dqn_cnn_handle *h, int64_t *bytes);
 
 #ifdef __cplusplus
 }
